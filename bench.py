@@ -32,6 +32,9 @@ Prints ONE JSON line (rank 0).  Extra objects:
   parity       — the device fit + predict_f at the base hyper-parameters against that oracle run (exit code 3 above 1e-5).
 Secondary objects carry their own `parity`: c4_single_gpu (solve residual on 512 oracle-rebuilt rows), grad and c5 (analytic
 directional derivative against a central difference of the device mll).
+
+`--dump-outputs DIR` writes what the last timed step computed (mll, alpha, mu, sigma2) as DIR/<name>.npy, so that two builds run with
+the same arguments (same seeded inputs) can be compared output for output.
 """
 import argparse
 import json
@@ -303,7 +306,9 @@ def run_workload(g, ctx, n, d, p, dtype, steps, warmup, barrier, comm=None, shar
     prof["stage"] = stage
     prof["stage_steps"] = warmup
     assert np.all(np.isfinite(mu)) and np.all(np.isfinite(s2)) and math.isfinite(gp.mll)
-    return {"elapsed": elapsed, "prof": prof, "syrk_bytes": syrk_bytes, "t_build": t_build, "mll": gp.mll, "ll": ll,
+    # what the last timed step handed its caller: update_mll! (mll, alpha) and predict_f (mean, variance) — --dump-outputs
+    outputs = {"mll": np.array([gp.mll], dtype=np.float64), "alpha": gp.alpha, "mu": mu, "sigma2": s2}
+    return {"elapsed": elapsed, "prof": prof, "syrk_bytes": syrk_bytes, "t_build": t_build, "mll": gp.mll, "ll": ll, "outputs": outputs,
             "fit_ms": 1e3 * wall["fit"] / steps, "predict_ms": 1e3 * wall["predict"] / steps,
             "base_mll": base_mll, "base_mu": np.asarray(base_mu, dtype=np.float64), "base_s2": np.asarray(base_s2, dtype=np.float64),
             "base_alpha": base_alpha}
@@ -556,6 +561,24 @@ def run_c5(g, ctx, n=1000000, m=4096, d=8):
     }
 
 
+DUMP_LIMIT_BYTES = 60_000_000   # under the 64 MB cap with room for the .npy headers
+
+
+def dump_outputs(dirname, outputs):
+    """--dump-outputs DIR: DIR/<name>.npy for every array of the last timed step, in float32 or float64.  The inputs are seeded, so two
+    builds run with the same arguments can be compared array for array.  Outputs larger than the limit in all are thinned to every
+    k-th entry (the same k for every array, fixed by the sizes alone)."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {}
+    for name, a in outputs.items():
+        a = np.asarray(a)
+        arrays[name] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+    stride = max(1, -(-sum(a.nbytes for a in arrays.values()) // DUMP_LIMIT_BYTES))
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a.reshape(-1)[::stride]))
+    return stride
+
+
 def _free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -585,7 +608,11 @@ def main():
     ap.add_argument("--mode", default=None, choices=["replicas", "sharded"],
                     help="N>1: ONE fit row-block sharded over the GPUs with the RCCL panel exchange (default, strong scaling) "
                          "or independent fits per GPU (replicas, weak scaling); N=1: sharded runs the sharded code path on one GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (mll, alpha, mu, sigma2) as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world_env = os.environ.get("WORLD_SIZE")
     if args.gpus > 1 and world_env is None:
@@ -704,6 +731,8 @@ def main():
         pass
     res = run_workload(g, ctx, n, d, p, args.dtype, args.steps, args.warmup, barrier, comm=make_comm() if sharded else None, sharded=sharded)
     elapsed = max_over_ranks(res["elapsed"])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res["outputs"])
 
     out = None
     if rank == 0:

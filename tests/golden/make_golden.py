@@ -8,7 +8,8 @@ the reference's relational tests (tests/test_oracle.py).  They freeze today's nu
 that later rounds cannot drift silently; they are not reference-produced goldens
 ("parity unpinned by reference outputs", DESIGN.md).
 
-Run from the repo root (needs /root/reference):  python tests/golden/make_golden.py
+Run from the repo root with the reference's input file:
+    python tests/golden/make_golden.py <reference checkout>/perf/benchmarks/simdata.csv
 """
 import os
 import sys
@@ -37,8 +38,7 @@ KERNS = {
 }
 
 
-def main():
-    csv = "/root/reference/perf/benchmarks/simdata.csv"
+def main(csv):
     data = np.loadtxt(csv, delimiter=",", skiprows=1)
     x = np.ascontiguousarray(data[:N, :10].T)  # d x N
     y = data[:N, 10].copy()
@@ -57,4 +57,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    main(sys.argv[1])
