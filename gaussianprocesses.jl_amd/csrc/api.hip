@@ -22,9 +22,11 @@ static bool is_ard(int op) {
     return op == GPMI_K_SE_ARD || op == GPMI_K_MAT12_ARD || op == GPMI_K_MAT32_ARD || op == GPMI_K_MAT52_ARD ||
            op == GPMI_K_RQ_ARD;
 }
+// Periodic (periodic.jl: Isotropic{Euclidean}) is an iso leaf of three parameters [l2, s2, p]: a function of |x - x'| only, with
+// k(x, x) = s2, so the scalar kdiag and the input centring of cov.hip hold for it.  (Lin / Poly are neither: DESIGN.md §7.)
 static bool is_iso(int op) {
     return op == GPMI_K_SE_ISO || op == GPMI_K_MAT12_ISO || op == GPMI_K_MAT32_ISO || op == GPMI_K_MAT52_ISO ||
-           op == GPMI_K_RQ_ISO;
+           op == GPMI_K_RQ_ISO || op == GPMI_K_PERIODIC;
 }
 
 int digest_kernel(const gpmi_kernel* k, int d, std::vector<unsigned char>* buf, std::string* err) {
@@ -78,7 +80,7 @@ int digest_kernel(const gpmi_kernel* k, int d, std::vector<unsigned char>* buf, 
             return GPMI_EARG;
         }
         const int nd = (d1 > d0) ? d1 - d0 : d;
-        const int npar = is_ard(op) ? nd + 1 + (op == GPMI_K_RQ_ARD) : is_iso(op) ? 2 + (op == GPMI_K_RQ_ISO) : 1;
+        const int npar = is_ard(op) ? nd + 1 + (op == GPMI_K_RQ_ARD) : is_iso(op) ? 2 + (op == GPMI_K_RQ_ISO || op == GPMI_K_PERIODIC) : 1;
         if (pp + npar > k->n_params) {
             *err = "kernel descriptor: params shorter than the program needs";
             return GPMI_EARG;
@@ -94,7 +96,8 @@ int digest_kernel(const gpmi_kernel* k, int d, std::vector<unsigned char>* buf, 
                 *err = "kernel descriptor: active dim out of range";
                 return GPMI_EARG;
             }
-            w[kk] += is_ard(op) ? par[z] : 1.0;
+            // Periodic: 1/p^2 folded into the weights, so the leaf sees t = r / p as the root of its weighted squared distance
+            w[kk] += is_ard(op) ? par[z] : (op == GPMI_K_PERIODIC) ? 1.0 / (par[2] * par[2]) : 1.0;
             if (is_ard(op)) out->pmtab()[lf.woff + kk] = (int32_t)z;
         }
         lf.poff = hyp;
@@ -108,6 +111,8 @@ int digest_kernel(const gpmi_kernel* k, int d, std::vector<unsigned char>* buf, 
             if (op == GPMI_K_RQ_ISO) {
                 lf.p1 = par[2];
                 lf.p0 = 1.0 / (2.0 * par[2] * par[0]);
+            } else if (op == GPMI_K_PERIODIC) {
+                lf.p0 = 2.0 / par[0];  // k = s2 exp(-p0 sin^2(pi t))
             } else {
                 lf.p0 = 1.0 / par[0];
             }
@@ -133,7 +138,8 @@ int digest_kernel(const gpmi_kernel* k, int d, std::vector<unsigned char>* buf, 
     }
     out->kdiag = kst[0];
     out->n_hyp = hyp;
-    // multi-leaf programs of shallow depth get the specialised interior-tile kernel (cov.hip)
+    // multi-leaf programs of shallow depth get the specialised interior-tile kernel (cov.hip); its FEAT bits switch on the leaves
+    // that need more than exp / sqrt (the Mauna Loa model, (SE + Periodic * SE) + RQ + SE, is depth 3 with bits 0 and 2)
     out->fast_class = -1;
     if (k->n_ops > 1) {
         int dep = 0, maxdep = 0, cls = 0;
@@ -145,6 +151,7 @@ int digest_kernel(const gpmi_kernel* k, int d, std::vector<unsigned char>* buf, 
                 ++dep;
                 if (op == GPMI_K_RQ_ISO || op == GPMI_K_RQ_ARD) cls |= 1;
                 if (op == GPMI_K_NOISE) cls |= 2;
+                if (op == GPMI_K_PERIODIC) cls |= 4;
             }
             maxdep = std::max(maxdep, dep);
         }

@@ -22,14 +22,14 @@ constexpr int SUPER = 8;      // tiles per super-tile edge (XCD-aware ordering)
 // ------------------------------------------------------------------------------------------
 // Device-side kernel program: the gpmi_kernel postfix descriptor, digested on the host.
 // Every leaf carries a DENSE weight vector over all d input rows (0 on rows a Masked
-// wrapper hides, il2[z] on active ARD rows, 1 on active iso rows), so the device loop
+// wrapper hides, il2[z] on active ARD rows, 1 on active iso rows, 1/p^2 on active Periodic rows), so the device loop
 // is the same for Masked / ARD / iso leaves:  r = sum_k w_k (x_k - y_k)^2.
 // ------------------------------------------------------------------------------------------
 struct DevLeaf {
     int32_t op;     // gpmi_op
     int32_t woff;   // offset of this leaf's d weights inside DevProgram::w (leaf ops only)
     double s2;      // signal variance
-    double p0;      // reciprocal constant: 1/l2 (SE iso), 1/l (Matern iso), 1/(2 a l2) (RQ iso), 0.5/a (RQ ard), 1 otherwise
+    double p0;      // reciprocal constant: 1/l2 (SE iso), 1/l (Matern iso), 1/(2 a l2) (RQ iso), 0.5/a (RQ ard), 2/l2 (Periodic), 1 otherwise
     double p1;      // RQ: alpha
     // gradient path (update_dmll!): tree structure and where this node's log-parameters sit in get_params order
     int32_t left, right;  // children of a SUM / PROD node (indices into leaf[])
@@ -41,7 +41,8 @@ struct DevProgram {
     int32_t d;
     int32_t has_noise_leaf;
     int32_t fast_class;  // >= 0: a multi-leaf program the specialised interior-tile kernel takes (cov.hip cov_multi_kernel): stationary /
-                         // Const / Noise leaves only, evaluation depth <= 3; bit 0 = an RQ leaf (pow), bit 1 = a Noise leaf.  -1 otherwise
+                         // Const / Noise leaves only, evaluation depth <= 3; bit 0 = an RQ leaf (pow), bit 1 = a Noise leaf, bit 2 = a
+                         // Periodic leaf (sin).  -1 otherwise
     double kdiag;  // k(x,x): the program evaluated with every leaf at r = 0
     int32_t n_hyp;  // total number of kernel hyper-parameters (get_params order)
     int32_t pad2_;

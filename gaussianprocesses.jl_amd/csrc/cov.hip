@@ -13,6 +13,7 @@
 //     (x-y)^2 per input row is computed once per entry and shared by all leaves;
 //   * nugget, identity padding and the lower-triangle tile skip are fused in.
 #include "common.h"
+#include "sinpi.h"
 
 namespace gpmi {
 
@@ -65,9 +66,10 @@ struct Tr<float> {
     static constexpr float isapprox_rtol = 3.4526698300124393e-04f;  // sqrt(eps(Float32))
 };
 
-// leaf cov(k, r): r is the (weighted) SQUARED distance; Matern leaves take its root
+// leaf cov(k, r): r is the (weighted) SQUARED distance; Matern and Periodic leaves take its root
 // (distij(::Euclidean) = sqrt, exact 0 on coincident points because r is exactly 0 there).
-template <typename T>
+// PER: the program has a Periodic leaf (programs without one compile as they did before it existed).
+template <typename T, bool PER>
 __device__ __forceinline__ T leaf_value(int op, T r, T s2, T p0inv, T p1) {
     switch (op) {
         case GPMI_K_SE_ISO: return s2 * Tr<T>::exp_((T(-0.5) * r) * p0inv);            // se_iso.jl:39
@@ -87,11 +89,18 @@ __device__ __forceinline__ T leaf_value(int op, T r, T s2, T p0inv, T p1) {
         case GPMI_K_RQ_ISO:                                                              // rq_iso.jl:44
         case GPMI_K_RQ_ARD:                                                              // rq_ard.jl:47
             return s2 * Tr<T>::pow_(T(1) + r * p0inv, -p1);
-        default: return s2;  // GPMI_K_CONST (const.jl:36)
+        default:
+            if constexpr (PER) {
+                if (op == GPMI_K_PERIODIC) {                                             // periodic.jl:45 (1/p^2 in the weights, p0 = 2/l2)
+                    const T sn = sinpi_mod1(Tr<T>::sqrt_(r));
+                    return s2 * Tr<T>::exp_(-(p0inv * (sn * sn)));
+                }
+            }
+            return s2;  // GPMI_K_CONST (const.jl:36)
     }
 }
 
-// Is this tile one the fast kernel takes?  One stationary leaf (the bench's SEArd; any single SE / Matern / RQ kernel) and a
+// Is this tile one the fast kernel takes?  One stationary leaf (the bench's SEArd; any single SE / Matern / RQ / Periodic kernel) and a
 // tile that needs neither padding nor the diagonal (nugget).  Both kernels evaluate it, so every tile has exactly one owner.
 __device__ __forceinline__ bool fast_tile(const DevProgram* __restrict__ prog, int nops, int flags, int64_t row0, int64_t col0,
                                           int TR, int TC, int64_t na, int64_t nb, int64_t nrows, int64_t ncols, int64_t row_off) {
@@ -118,7 +127,7 @@ __device__ __forceinline__ bool fast_tile(const DevProgram* __restrict__ prog, i
 // the row operand comes through SCALAR loads (the row pointer is wave-uniform: s_load_dwordx8/16, no LDS, no barrier), the column
 // operand is loaded once per wave into registers (this lane's VEC columns: DMAX contiguous elements each), two rows per iteration
 // for instruction-level parallelism.  Same tiles, same owner rule (fast_tile) and the same 1 KiB-per-row wavefront stores as before.
-enum LeafFamily { FAM_SE = 0, FAM_MAT12 = 1, FAM_MAT32 = 2, FAM_MAT52 = 3, FAM_RQ = 4 };
+enum LeafFamily { FAM_SE = 0, FAM_MAT12 = 1, FAM_MAT32 = 2, FAM_MAT52 = 3, FAM_RQ = 4, FAM_PERIODIC = 5 };
 
 template <int DMAX>
 struct ScaleW {
@@ -183,7 +192,8 @@ __device__ __forceinline__ double sqrt_nonneg(double r) {
 }
 __device__ __forceinline__ float sqrt_nonneg(float r) { return sqrtf(r); }
 
-// the leaf function on the squared distance of the PRE-SCALED inputs (file header of each kernel in include/gpmi.h)
+// the leaf function on the squared distance of the PRE-SCALED inputs (file header of each kernel in include/gpmi.h); p1 is RQ's alpha,
+// Periodic's 2/l2
 template <typename T, int FAM>
 __device__ __forceinline__ T leaf_family(T r, T s2, T p1) {
     if constexpr (FAM == FAM_SE) {
@@ -196,8 +206,11 @@ __device__ __forceinline__ T leaf_family(T r, T s2, T p1) {
     } else if constexpr (FAM == FAM_MAT52) {
         const T s = sqrt_nonneg(r);                                             // mat52_*.jl (5/l^2 in the weights): 1 + s + s^2/3
         return s2 * Tr<T>::fma_(s, Tr<T>::fma_(s, T(1.0 / 3.0), T(1)), T(1)) * Tr<T>::exp_(-s);
-    } else {
+    } else if constexpr (FAM == FAM_RQ) {
         return s2 * Tr<T>::pow_(T(1) + r, -p1);                                 // rq_*.jl (1/(2 a l2) resp. 0.5/a in the weights)
+    } else {
+        const T sn = sinpi_mod1(sqrt_nonneg(r));                                // periodic.jl:45 (1/p^2 in the weights): t = r/p
+        return s2 * Tr<T>::exp_(-(p1 * (sn * sn)));
     }
 }
 
@@ -266,7 +279,8 @@ __global__ __launch_bounds__(256) void cov_leaf_kernel(const T* __restrict__ xas
 // through scalar loads, the column operand straight into registers — no LDS transposition, no barrier after the prologue), every
 // leaf's parameters and weights sit in LDS in the element type (one broadcast read per use instead of an SMEM round trip), TWO rows
 // per pass over the program (the wave-uniform control flow is paid once per four / eight entries of a lane), sqrt by rsq + Goldschmidt.
-// No fp64 pow unless the program has an RQ leaf (FEAT & 1: the library routine alone costs ~90 VGPRs); the Noise leaf (FEAT & 2)
+// No fp64 pow unless the program has an RQ leaf (FEAT & 1: the library routine alone costs ~90 VGPRs), no sine polynomial unless it has
+// a Periodic leaf (FEAT & 4: programs without one compile as before); the Noise leaf (FEAT & 2)
 // behind a prefilter: noise.jl:31-37 asks x_z ~ y_z for every active row z (isapprox, rtol sqrt(eps)), which needs
 // (x_z - y_z)^2 <= (rtol max|x|)^2 for all z — one v_max per row on the squared differences the other leaves need anyway; the exact
 // test runs only where some lane of the wave passes it (coincident points: the diagonal, duplicates).
@@ -486,7 +500,19 @@ __global__ __launch_bounds__(256) void cov_multi_kernel(const T* __restrict__ xa
                                 val[i][q] = sig2 * (T(1) + sv + sv * sv * T(1.0 / 3.0)) * Tr<T>::exp_(-sv);
                             }
                         break;
-                    default:  // GPMI_K_RQ_*
+                    default:  // GPMI_K_RQ_*, GPMI_K_PERIODIC
+                        if constexpr (FEAT & 4) {  // periodic.jl:45 (1/p^2 in the weights, p0 = 2/l2)
+                            if (op == GPMI_K_PERIODIC) {
+#pragma unroll
+                                for (int i = 0; i < NR; ++i)
+#pragma unroll
+                                    for (int q = 0; q < VEC; ++q) {
+                                        const T sn = sinpi_mod1(sqrt_nonneg(r[i][q]));
+                                        val[i][q] = sig2 * Tr<T>::exp_(-(p0inv * (sn * sn)));
+                                    }
+                                break;
+                            }
+                        }
                         if constexpr (FEAT & 1) {
 #pragma unroll
                             for (int i = 0; i < NR; ++i)
@@ -520,7 +546,7 @@ __global__ __launch_bounds__(256) void cov_multi_kernel(const T* __restrict__ xa
     }
 }
 
-template <typename T, int DMAX>
+template <typename T, int DMAX, bool PER>
 __global__ __launch_bounds__(256) void cov_kernel(const T* __restrict__ xa, int64_t na, const T* __restrict__ xb,
                                                   int64_t nb, int d, T* __restrict__ C, int64_t ldc, int64_t nrows,
                                                   int64_t ncols, const DevProgram* __restrict__ prog, int flags,
@@ -699,7 +725,7 @@ __global__ __launch_bounds__(256) void cov_kernel(const T* __restrict__ xa, int6
                 const T p0inv = (T)prog->leaf[o].p0;
                 const T p1 = (T)prog->leaf[o].p1;
 #pragma unroll
-                for (int q = 0; q < VEC; ++q) val[q] = leaf_value<T>(op, r[q], s2, p0inv, p1);
+                for (int q = 0; q < VEC; ++q) val[q] = leaf_value<T, PER>(op, r[q], s2, p0inv, p1);
             }
             // push
 #pragma unroll
@@ -742,9 +768,11 @@ void launch_cov_t(gpmi_ctx* ctx, const T* xa, int64_t na, const T* xb, int64_t n
         lds = 0;
         flags |= COV_GLOBAL_X;
     }
-    auto kern = cov_kernel<T, DMAX>;
-    if (lds > 48 * 1024) hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     const DevProgram* hp = ctx->h_prog;
+    bool periodic = false;
+    for (int o = 0; o < hp->n_ops; ++o) periodic = periodic || hp->leaf[o].op == GPMI_K_PERIODIC;
+    auto kern = periodic ? cov_kernel<T, DMAX, true> : cov_kernel<T, DMAX, false>;
+    if (lds > 48 * 1024) hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     bool single_leaf = false, multi = false;
     T *xas = nullptr, *xbs = nullptr;
     unsigned long long* amax = nullptr;
@@ -777,6 +805,7 @@ void launch_cov_t(gpmi_ctx* ctx, const T* xa, int64_t na, const T* xb, int64_t n
                 case GPMI_K_MAT32_ISO: case GPMI_K_MAT32_ARD: fam = FAM_MAT32; mult = 3.0 * lf.p0 * lf.p0; break;
                 case GPMI_K_MAT52_ISO: case GPMI_K_MAT52_ARD: fam = FAM_MAT52; mult = 5.0 * lf.p0 * lf.p0; break;
                 case GPMI_K_RQ_ISO: case GPMI_K_RQ_ARD: fam = FAM_RQ; break;
+                case GPMI_K_PERIODIC: fam = FAM_PERIODIC; mult = 1.0; break;  // 1/p^2 is in the weights already; p0 = 2/l2 goes as p1
                 default: break;
             }
             ScaleW<DMAX> sw;
@@ -789,13 +818,14 @@ void launch_cov_t(gpmi_ctx* ctx, const T* xa, int64_t na, const T* xb, int64_t n
                                    (unsigned long long*)nullptr, xb);
                 auto go = [&](auto lk) {
                     hipLaunchKernelGGL(lk, grid, dim3(256), 0, ctx->stream, (const T*)xas, na, (const T*)xbs, nb, C, ldc, nrows_total, ncols_total,
-                                       ctx->d_prog, flags, row_off, (T)lf.s2, (T)lf.p1);
+                                       ctx->d_prog, flags, row_off, (T)lf.s2, (T)(fam == FAM_PERIODIC ? lf.p0 : lf.p1));
                 };
                 switch (fam) {
                     case FAM_SE: go(cov_leaf_kernel<T, DMAX, FAM_SE>); break;
                     case FAM_MAT12: go(cov_leaf_kernel<T, DMAX, FAM_MAT12>); break;
                     case FAM_MAT32: go(cov_leaf_kernel<T, DMAX, FAM_MAT32>); break;
                     case FAM_MAT52: go(cov_leaf_kernel<T, DMAX, FAM_MAT52>); break;
+                    case FAM_PERIODIC: go(cov_leaf_kernel<T, DMAX, FAM_PERIODIC>); break;
                     default: go(cov_leaf_kernel<T, DMAX, FAM_RQ>); break;
                 }
             }
@@ -814,7 +844,11 @@ void launch_cov_t(gpmi_ctx* ctx, const T* xa, int64_t na, const T* xb, int64_t n
                 case 0: go(cov_multi_kernel<T, DMAX, 0>); break;
                 case 1: go(cov_multi_kernel<T, DMAX, 1>); break;
                 case 2: go(cov_multi_kernel<T, DMAX, 2>); break;
-                default: go(cov_multi_kernel<T, DMAX, 3>); break;
+                case 3: go(cov_multi_kernel<T, DMAX, 3>); break;
+                case 4: go(cov_multi_kernel<T, DMAX, 4>); break;
+                case 5: go(cov_multi_kernel<T, DMAX, 5>); break;
+                case 6: go(cov_multi_kernel<T, DMAX, 6>); break;
+                default: go(cov_multi_kernel<T, DMAX, 7>); break;
             }
         }
     }

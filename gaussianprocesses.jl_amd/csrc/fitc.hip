@@ -524,7 +524,7 @@ int fitc_grad_t(gpmi_fitc* f, const gpmi_kernel* k, double log_noise, double* dk
     // on x).  A non-stationary leaf (Lin, Poly, ...) added to gpmi_op must be weighted per point here: refuse it until then.
     for (int o = 0; o < c->h_prog->n_ops; ++o) {
         const int op = c->h_prog->leaf[o].op;
-        if (!((op >= GPMI_K_SE_ISO && op <= GPMI_K_CONST) || op == GPMI_K_SUM || op == GPMI_K_PROD)) {
+        if (!((op >= GPMI_K_SE_ISO && op <= GPMI_K_PERIODIC) || op == GPMI_K_SUM || op == GPMI_K_PROD)) {
             c->err = "gpmi_fitc_grad: the diagonal term assumes stationary leaves; this kernel has a leaf outside that set";
             return GPMI_EARG;
         }

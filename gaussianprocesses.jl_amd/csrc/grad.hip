@@ -9,11 +9,14 @@
 //     and reduces  sum_{i>=j} W_ij dK_ij/dθ_p (diagonal counted half) without ever forming an N x N x p stack:
 //     per leaf one forward-mode sweep of the postfix program (product rule of prod_kernel.jl:17-68, sum rule of
 //     sum_kernel.jl:18-51) on a register stack, then that leaf's closed-form derivatives
-//     (se_iso.jl:41-50, se_ard.jl:45-54, mat.jl:5-33 + mat*_*.jl, rq_iso.jl:45-61, rq_ard.jl:48-63, noise.jl:47,
-//     const.jl:40).  Per-thread accumulators live in LDS ([slot][thread], conflict-free); block partials are
+//     (se_iso.jl:41-50, se_ard.jl:45-54, mat.jl:5-33 + mat*_*.jl, rq_iso.jl:45-61, rq_ard.jl:48-63, periodic.jl:48-64,
+//     noise.jl:47, const.jl:40).  Per-thread accumulators live in LDS ([slot][thread], conflict-free); block partials are
 //     summed by a second kernel in a fixed order, so the gradient is bit-reproducible.
 // The trace of W (noise gradient) rides along as one more slot.
+#include <type_traits>
+
 #include "common.h"
+#include "sinpi.h"
 
 namespace gpmi {
 
@@ -55,7 +58,8 @@ __device__ __forceinline__ bool is_ard_op(int op) {
 // [slot][thread] LDS table: the pair's differences are re-read from global memory (L1 / L2) wherever they are used, and every
 // contribution is reduced across the wave at once (shuffles: a fixed order, so still bit-reproducible) into a [wave][slot] table.
 // Several times slower per pair than the register forms; it only runs for d > 32 or more than 64 hyper-parameters.
-template <typename T, int DMAX, bool RECT>
+// PER: the program has a Periodic leaf (programs without one compile as they did before it existed).
+template <typename T, int DMAX, bool RECT, bool PER>
 __global__ __launch_bounds__(256) void dmll_kernel(const T* __restrict__ x, int64_t n, int d, const T* __restrict__ alpha,
                                                    const T* __restrict__ Kinv, int64_t ld,
                                                    const DevProgram* __restrict__ prog, double* __restrict__ partial,
@@ -212,7 +216,16 @@ __global__ __launch_bounds__(256) void dmll_kernel(const T* __restrict__ x, int6
                             const T s = T(2.2360679774997896964) * GM<T>::sqrt_(r2) * p0;
                             v = s2 * (T(1) + s + s * s * T(1.0 / 3.0)) * GM<T>::exp_(-s);
                         } break;
-                        default: v = s2 * GM<T>::pow_(T(1) + r2 * p0, -al); break;  // RQ iso / ard
+                        default:
+                            if constexpr (PER) {
+                                if (op == GPMI_K_PERIODIC) {  // periodic.jl:45, 1/p^2 in the weights: sqrt(r2) = r/p
+                                    const T sn = sinpi_mod1(GM<T>::sqrt_(r2));
+                                    v = s2 * GM<T>::exp_(-(p0 * (sn * sn)));
+                                    break;
+                                }
+                            }
+                            v = s2 * GM<T>::pow_(T(1) + r2 * p0, -al);  // RQ iso / ard
+                            break;
                     }
                 }
                 if (o == L) {
@@ -243,6 +256,15 @@ __global__ __launch_bounds__(256) void dmll_kernel(const T* __restrict__ x, int6
             // length-scale derivative = c * (r2 for iso | w_k dsq_k for ARD dim k)
             T c;
             const T re = GM<T>::sqrt_(r2);
+            if constexpr (PER) {
+                if (op == GPMI_K_PERIODIC) {  // periodic.jl:48-51 with t = r/p, s = p0 sin^2(pi t), p0 = 2/l2: dk_dll = 2 s k, dk_dlp = k p0 pi t sin(2 pi t)
+                    T sn, cs;
+                    sincospi_mod1(re, &sn, &cs);
+                    acc(poff, (double)(a * T(2) * (p0 * (sn * sn)) * kv));
+                    acc(sig + 1, (double)(a * kv * p0 * (T(3.14159265358979323846) * re) * (T(2) * sn * cs)));
+                    continue;
+                }
+            }
             switch (op) {
                 case GPMI_K_SE_ISO: c = kv * p0; break;                         // r/l2 * k
                 case GPMI_K_SE_ARD: c = kv; break;                              // wdiff * k
@@ -346,16 +368,26 @@ static int64_t launch_dmll_any(gpmi_ctx* ctx, const T* x, int64_t n, int d, cons
         if (lds > 48 * 1024) hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL(kern, dim3(ntc, ntr), dim3(256), lds, ctx->stream, x, n, d, alpha, Kinv, ld, ctx->d_prog, partial, n_hyp, xb, nb);
     };
-    if (gen)
-        go(dmll_kernel<T, 0, RECT>);
-    else if (d <= 4)
-        go(dmll_kernel<T, 4, RECT>);
-    else if (d <= 8)
-        go(dmll_kernel<T, 8, RECT>);
-    else if (d <= 16)
-        go(dmll_kernel<T, 16, RECT>);
+    const DevProgram* hp = ctx->h_prog;
+    bool periodic = false;
+    for (int o = 0; o < hp->n_ops; ++o) periodic = periodic || hp->leaf[o].op == GPMI_K_PERIODIC;
+    auto pick = [&](auto per) {
+        constexpr bool PER = decltype(per)::value;
+        if (gen)
+            go(dmll_kernel<T, 0, RECT, PER>);
+        else if (d <= 4)
+            go(dmll_kernel<T, 4, RECT, PER>);
+        else if (d <= 8)
+            go(dmll_kernel<T, 8, RECT, PER>);
+        else if (d <= 16)
+            go(dmll_kernel<T, 16, RECT, PER>);
+        else
+            go(dmll_kernel<T, 32, RECT, PER>);
+    };
+    if (periodic)
+        pick(std::true_type{});
     else
-        go(dmll_kernel<T, 32, RECT>);
+        pick(std::false_type{});
     return (int64_t)ntr * ntc;
 }
 template <typename T>

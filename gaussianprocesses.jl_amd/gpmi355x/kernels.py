@@ -9,6 +9,7 @@ interchangeable:
     Mat12/32/52Ard     src/kernels/mat*_ard.jl:31      fields iℓ2[], σ2
     RQIso(ll, lσ, lα)  src/kernels/rq_iso.jl:33        fields ℓ2, σ2, α
     RQArd(ll[],lσ,lα)  src/kernels/rq_ard.jl:34        fields iℓ2[], σ2, α
+    Periodic(ll,lσ,lp) src/kernels/periodic.jl:33      fields ℓ2, σ2, p
     Noise(lσ)          src/kernels/noise.jl:27         field σ2
     Const(lσ)          src/kernels/const.jl:25         field σ2
     SumKernel / ProdKernel (`+`, `*`)  src/kernels/sum_kernel.jl, prod_kernel.jl, pair_kernel.jl:14-24
@@ -29,7 +30,7 @@ from . import _lib
 
 OP = {
     "SEIso": 1, "SEArd": 2, "Mat12Iso": 3, "Mat12Ard": 4, "Mat32Iso": 5, "Mat32Ard": 6,
-    "Mat52Iso": 7, "Mat52Ard": 8, "RQIso": 9, "RQArd": 10, "Noise": 11, "Const": 12,
+    "Mat52Iso": 7, "Mat52Ard": 8, "RQIso": 9, "RQArd": 10, "Noise": 11, "Const": 12, "Periodic": 13,
 }
 OP_SUM, OP_PROD = 100, 101
 
@@ -206,6 +207,24 @@ class RQArd(_Leaf):
         self._emit(d, active, ops, dims_off, dims, params, self.il2 + [self.s2, self.alpha])
 
 
+class Periodic(_Leaf):
+    """Periodic(ll, lσ, lp) — periodic.jl:33: σ2·exp(−2/ℓ2·sin²(π r/p)), r the Euclidean distance."""
+
+    def __init__(self, ll, lsig, lp):
+        self.set_params([ll, lsig, lp])
+
+    def set_params(self, hyp):  # periodic.jl:39-43
+        if len(hyp) != 3:
+            raise _lib.ArgumentError(f"Periodic function has three parameters, received {len(hyp)}.")
+        self.l2, self.s2, self.p = math.exp(2.0 * hyp[0]), math.exp(2.0 * hyp[1]), math.exp(hyp[2])
+
+    def get_params(self):
+        return [math.log(self.l2) / 2.0, math.log(self.s2) / 2.0, math.log(self.p)]
+
+    def _flatten(self, d, active, ops, dims_off, dims, params):
+        self._emit(d, active, ops, dims_off, dims, params, [self.l2, self.s2, self.p])
+
+
 class _Scalar(_Leaf):
     def __init__(self, lsig):
         self.set_params([lsig])
@@ -365,6 +384,6 @@ def from_spec(spec):
     table = {
         "se_iso": SEIso, "se_ard": SEArd, "mat12_iso": Mat12Iso, "mat12_ard": Mat12Ard,
         "mat32_iso": Mat32Iso, "mat32_ard": Mat32Ard, "mat52_iso": Mat52Iso, "mat52_ard": Mat52Ard,
-        "rq_iso": RQIso, "rq_ard": RQArd, "noise": Noise, "const": Const,
+        "rq_iso": RQIso, "rq_ard": RQArd, "noise": Noise, "const": Const, "periodic": Periodic,
     }
     return table[name](*spec[1:])

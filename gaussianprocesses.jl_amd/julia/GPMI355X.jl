@@ -81,6 +81,7 @@ flatten!(kd, k::RQIso, a)    = leaf!(kd, 9, a, [k.ℓ2, k.σ2, k.α])
 flatten!(kd, k::RQArd, a)    = leaf!(kd, 10, a, [k.iℓ2; k.σ2; k.α])
 flatten!(kd, k::Noise, a)    = leaf!(kd, 11, a, [k.σ2])
 flatten!(kd, k::Const, a)    = leaf!(kd, 12, a, [k.σ2])
+flatten!(kd, k::Periodic, a) = leaf!(kd, 13, a, [k.ℓ2, k.σ2, k.p])
 function flatten!(kd, k::Union{SumKernel,ProdKernel}, a)
     flatten!(kd, k.kleft, a); flatten!(kd, k.kright, a)
     push!(kd.ops, k isa SumKernel ? 100 : 101); push!(kd.dims_off, length(kd.dims))

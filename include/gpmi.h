@@ -63,6 +63,7 @@ enum gpmi_op {
     GPMI_K_RQ_ARD = 10,    /* src/kernels/rq_ard.jl:47     s2*(1+0.5 r/a)^-a                         params [il2[nd], s2, a]*/
     GPMI_K_NOISE = 11,     /* src/kernels/noise.jl:29-39   s2*[all_z x_z ~= y_z]  (isapprox, rtol sqrt(eps)) params [s2]    */
     GPMI_K_CONST = 12,     /* src/kernels/const.jl:36      s2                                        params [s2]            */
+    GPMI_K_PERIODIC = 13,  /* src/kernels/periodic.jl:45   s2*exp(-2/l2 sin^2(pi r/p)), r = euclid   params [l2, s2, p]     */
     GPMI_K_SUM = 100,      /* src/kernels/sum_kernel.jl:15  pops right, left; pushes left+right                             */
     GPMI_K_PROD = 101      /* src/kernels/prod_kernel.jl:14 pops right, left; pushes left*right                             */
 };
@@ -75,7 +76,7 @@ enum gpmi_op {
  *                       (fixed_kernel.jl:69) does not change cov and needs no encoding.
  *   params[n_params]    the kernels' STORED (transformed) fields in program order,
  *                       exactly the struct fields of the reference types (l2 | l |
- *                       il2[], s2, a) so host and device evaluate the same expression.
+ *                       il2[], s2, a, p) so host and device evaluate the same expression.
  *                       nd = size of the leaf's active-dim range (d when empty). */
 typedef struct gpmi_kernel {
     int32_t n_ops;
