@@ -386,7 +386,7 @@ static int fit_t(gpmi_gp* gp, const gpmi_kernel* k, const double* log_noise, int
 // gradient of the mll with respect to the kernel hyper-parameters and log-noise (update_dmll!, GPE.jl:298-324)
 // the gradient / predict_LOO scratch: two more npad x ld matrices (L^-T rows and K^-1), kept until gpmi_gp_destroy.  They
 // triple the model's footprint — N = 150 000 fp64 would need 540 GB — so failure here gets a message of its own.
-static int alloc_grad_scratch(gpmi_gp* gp, size_t bytes) {
+int alloc_grad_scratch(gpmi_gp* gp, size_t bytes) {
     gpmi_ctx* c = gp->ctx;
     for (void** p : {&gp->g1, &gp->g2}) {
         if (*p) continue;
@@ -410,18 +410,53 @@ static std::vector<WhitenSeg<T>> whiten_segments(const gpmi_gp* gp) {
     return v;
 }
 
+// W = (K + noise)^-1 in the lower tiles of G2 (gpmi_grad; the cross-validation entry points of cv.hip start from it too)
+template <typename T>
+bool build_kinv(gpmi_gp* gp) {
+    gpmi_ctx* c = gp->ctx;
+    const int64_t npad = gp->npad, ld = gp->ld;
+    const T* A = (const T*)gp->A;
+    T* G1 = (T*)gp->g1;
+    T* G2 = (T*)gp->g2;
+    // rows of L^-T: the whiten sequence applied to an identity (in G2, consumed); row i is zero left of column i,
+    // so block k only has to process rows < kend
+    launch_set_identity<T>(c, G2, ld, npad);
+    const auto segs = whiten_segments<T>(gp);
+    whiten_rows_inv<T>(c, A, ld, (const T*)gp->linv256, npad, G2, ld, G1, ld, [](int64_t kend) { return kend; }, &segs);
+    // K^-1 = L^-T L^-1 = G1 G1'  (lower tiles).  Small n: one product whose K loop starts at the tile's first row (G1 is
+    // upper triangular by rows).  Large n: the K dimension in chunks of 2048 columns — a tile's K loop over the whole
+    // row length streams two 128 x n panels (25 MB each at n = 50 000) through a 4 MB L2, chunked it is the K = 2048
+    // update of the factorisation: chunk c first WRITES the rows that start inside it (rows [k0, k1), K from the tile's
+    // first row), then accumulates onto the k0 x k0 block above them.  The accumulation subtracts, so G2 holds -K^-1.
+    const int64_t WK = c->grad_chunk;
+    const bool chunked = WK > 0 && npad >= 4 * WK;
+    if (!chunked) {
+        launch_gemm_shape<T>(c, G2, ld, G1, ld, G1, ld, npad, npad, npad, TileShape{0, 0, 1, 0, 1, 0}, nullptr,
+                             GEMM_OVERWRITE | GEMM_KSTART_ROW);
+    } else {
+        for (int64_t k0 = 0; k0 < npad; k0 += WK) {
+            const int64_t kw = std::min<int64_t>(WK, npad - k0), k1 = k0 + kw;
+            launch_gemm_shape<T>(c, G2 + k0 * ld, ld, G1 + k0 * ld + k0, ld, G1 + k0, ld, kw, k1, kw,
+                                 TileShape{0, 0, 1, (int)(k0 / GEMM_BM), 1, 0}, nullptr, GEMM_OVERWRITE | GEMM_NEGOUT | GEMM_KSTART_ROW);
+            if (k0 > 0)
+                launch_gemm_shape<T>(c, G2, ld, G1 + k0, ld, G1 + k0, ld, k0, k0, kw, TileShape{0, 0, 1, 0, 1, 0}, nullptr, GEMM_AUX);
+        }
+    }
+    return chunked;
+}
+template bool build_kinv<double>(gpmi_gp*);
+template bool build_kinv<float>(gpmi_gp*);
+
 template <typename T>
 static int grad_t(gpmi_gp* gp, const gpmi_kernel* k, const double* log_noise, double* dkern_out, double* dnoise_out) {
     gpmi_ctx* c = gp->ctx;
     const int64_t n = gp->n, npad = gp->npad, ld = gp->ld;
-    const T* A = (const T*)gp->A;
     la_reset(c);
     int rc = upload_program(c, k, gp->d);
     if (rc != GPMI_OK) return rc;
     const int n_hyp = c->h_prog->n_hyp;
     const size_t bytes = (size_t)(npad * ld) * sizeof(T);
     if (const int rc_g = alloc_grad_scratch(gp, bytes)) return rc_g;
-    T* G1 = (T*)gp->g1;
     T* G2 = (T*)gp->g2;
     const int64_t nt = (n + 63) / 64;
     const int64_t need = nt * nt * (n_hyp + 1) * (int64_t)sizeof(double);
@@ -434,30 +469,7 @@ static int grad_t(gpmi_gp* gp, const gpmi_kernel* k, const double* log_noise, do
     }
     {
         ProfScope ps(c, GPMI_PROF_SOLVE, 2.0 * (double)npad * (double)npad * (double)npad / 3.0);
-        // rows of L^-T: the whiten sequence applied to an identity (in G2, consumed); row i is zero left of column i,
-        // so block k only has to process rows < kend
-        launch_set_identity<T>(c, G2, ld, npad);
-        const auto segs = whiten_segments<T>(gp);
-        whiten_rows_inv<T>(c, A, ld, (const T*)gp->linv256, npad, G2, ld, G1, ld, [](int64_t kend) { return kend; }, &segs);
-        // K^-1 = L^-T L^-1 = G1 G1'  (lower tiles).  Small n: one product whose K loop starts at the tile's first row (G1 is
-        // upper triangular by rows).  Large n: the K dimension in chunks of 2048 columns — a tile's K loop over the whole
-        // row length streams two 128 x n panels (25 MB each at n = 50 000) through a 4 MB L2, chunked it is the K = 2048
-        // update of the factorisation: chunk c first WRITES the rows that start inside it (rows [k0, k1), K from the tile's
-        // first row), then accumulates onto the k0 x k0 block above them.  The accumulation subtracts, so G2 holds -K^-1.
-        const int64_t WK = c->grad_chunk;
-        const bool chunked = WK > 0 && npad >= 4 * WK;
-        if (!chunked) {
-            launch_gemm_shape<T>(c, G2, ld, G1, ld, G1, ld, npad, npad, npad, TileShape{0, 0, 1, 0, 1, 0}, nullptr,
-                                 GEMM_OVERWRITE | GEMM_KSTART_ROW);
-        } else {
-            for (int64_t k0 = 0; k0 < npad; k0 += WK) {
-                const int64_t kw = std::min<int64_t>(WK, npad - k0), k1 = k0 + kw;
-                launch_gemm_shape<T>(c, G2 + k0 * ld, ld, G1 + k0 * ld + k0, ld, G1 + k0, ld, kw, k1, kw,
-                                     TileShape{0, 0, 1, (int)(k0 / GEMM_BM), 1, 0}, nullptr, GEMM_OVERWRITE | GEMM_NEGOUT | GEMM_KSTART_ROW);
-                if (k0 > 0)
-                    launch_gemm_shape<T>(c, G2, ld, G1 + k0, ld, G1 + k0, ld, k0, k0, kw, TileShape{0, 0, 1, 0, 1, 0}, nullptr, GEMM_AUX);
-            }
-        }
+        const bool chunked = build_kinv<T>(gp);
         const int64_t nblocks = launch_dmll<T>(c, (const T*)gp->x, n, gp->d, (const T*)gp->alpha, G2, ld, gp->gpart, n_hyp, chunked);
         launch_reduce_partials(c, gp->gpart, nblocks, n_hyp + 1, (double*)gp->g1);  // g1 is free again: result vector
     }
@@ -908,7 +920,7 @@ void gpmi_gp_destroy(gpmi_gp* gp) {
         return;
     }
     void* ptrs[] = {gp->x, gp->A, gp->ymu, gp->alpha, gp->invdiag, gp->linv, gp->linv256, gp->noise, gp->rows, gp->xp, gp->small, gp->supinv,
-                    gp->g1, gp->g2, gp->gpart};
+                    gp->g1, gp->g2, gp->gpart, gp->cv, gp->cvblk};
     for (void* p : ptrs)
         if (p) hipFree(p);
     delete gp;
@@ -1098,6 +1110,94 @@ int gpmi_inv_diag(gpmi_gp* gp, void* out) {
         return rcb;
     }
     return gp->dtype == 64 ? gpmi::inv_diag_t<double>(gp, out) : gpmi::inv_diag_t<float>(gp, out);
+}
+
+// ---- cross-validation (cv.hip) ----
+static int cv_check(gpmi_gp* gp, const char* who, const gpmi_kernel* k, const double* log_noise, int64_t n_noise, int32_t n_kern,
+                    bool want_noise, bool folds, int64_t n_folds, const int64_t* fold_ptr, const int64_t* fold_idx) {
+    if (!gp) return GPMI_EARG;
+    gpmi_ctx* c = gp->ctx;
+    if (gp->group || blocked_of(gp)) {
+        c->err = std::string(who) + ": dense exact handle only (not provided on blocked / sharded handles)";
+        return GPMI_EARG;
+    }
+    if (int rc = need_fit(gp, who, false)) return rc;
+    if (k) {  // the gradient entry points (gpmi_grad's checks)
+        if (!log_noise || (n_noise != 1 && n_noise != gp->n)) {
+            c->err = std::string(who) + ": bad argument";
+            return GPMI_EARG;
+        }
+        if (n_noise != 1 && want_noise) {
+            c->err = std::string(who) + ": the noise gradient is defined for scalar logNoise only (GPE.jl:313)";
+            return GPMI_EARG;
+        }
+        std::string err;
+        std::vector<unsigned char> tmpb;
+        if (digest_kernel(k, gp->d, &tmpb, &err) != GPMI_OK || reinterpret_cast<const DevProgram*>(tmpb.data())->n_hyp != n_kern) {
+            c->err = err.empty() ? std::string(who) + ": dkern_out length differs from the kernel's number of parameters" : err;
+            return GPMI_EARG;
+        }
+        if (n_kern > GPMI_GRAD_MAX_PARAMS) return earg(c, "cross-validation: more than GPMI_GRAD_MAX_PARAMS (5000) kernel hyper-parameters");
+    }
+    if (!folds) return GPMI_OK;
+    if (n_folds <= 0 || !fold_ptr || !fold_idx || fold_ptr[0] != 0) {
+        c->err = std::string(who) + ": bad folds (n_folds >= 1, fold_ptr[0] = 0)";
+        return GPMI_EARG;
+    }
+    std::vector<char> seen((size_t)gp->n, 0);
+    for (int64_t f = 0; f < n_folds; ++f) {
+        const int64_t s = fold_ptr[f + 1] - fold_ptr[f];
+        if (s <= 0) {
+            c->err = std::string(who) + ": fold " + std::to_string(f) + " is empty";
+            return GPMI_EARG;
+        }
+        if (s > GPMI_CV_MAX_FOLD) {
+            c->err = std::string(who) + ": fold " + std::to_string(f) + " has " + std::to_string(s) +
+                     " indices; at most GPMI_CV_MAX_FOLD (2048, the super-panel width) are supported";
+            return GPMI_EARG;
+        }
+        for (int64_t e = fold_ptr[f]; e < fold_ptr[f + 1]; ++e) {
+            const int64_t i = fold_idx[e];
+            if (i < 0 || i >= gp->n) {
+                c->err = std::string(who) + ": fold index " + std::to_string(i) + " out of range";
+                return GPMI_EARG;
+            }
+            if (seen[(size_t)i]) {
+                c->err = std::string(who) + ": folds overlap at index " + std::to_string(i);
+                return GPMI_EARG;
+            }
+            seen[(size_t)i] = 1;
+        }
+    }
+    return GPMI_OK;
+}
+
+int gpmi_loo_grad(gpmi_gp* gp, const gpmi_kernel* k, const double* log_noise, int64_t n_noise, double* logp_out, double* dkern_out,
+                  int32_t n_kern, double* dnoise_out) {
+    if (!gp || !k) return earg((gp ? gp->ctx : nullptr), "gpmi_loo_grad: bad argument");
+    if (int rc = cv_check(gp, "gpmi_loo_grad", k, log_noise, n_noise, n_kern, dnoise_out != nullptr, false, 0, nullptr, nullptr)) return rc;
+    GPMI_HIP(gp->ctx, hipSetDevice(gp->ctx->device));
+    return gp->dtype == 64 ? cv_run<double>(gp, 0, k, log_noise, 0, nullptr, nullptr, logp_out, dkern_out, dnoise_out, nullptr, nullptr)
+                           : cv_run<float>(gp, 0, k, log_noise, 0, nullptr, nullptr, logp_out, dkern_out, dnoise_out, nullptr, nullptr);
+}
+
+int gpmi_cvfold_predict(gpmi_gp* gp, int64_t n_folds, const int64_t* fold_ptr, const int64_t* fold_idx, void* resid_out, void* cov_out,
+                        double* logp_out) {
+    if (!gp) return earg(nullptr, "gpmi_cvfold_predict: bad argument");
+    if (int rc = cv_check(gp, "gpmi_cvfold_predict", nullptr, nullptr, 0, 0, false, true, n_folds, fold_ptr, fold_idx)) return rc;
+    GPMI_HIP(gp->ctx, hipSetDevice(gp->ctx->device));
+    return gp->dtype == 64 ? cv_run<double>(gp, 1, nullptr, nullptr, n_folds, fold_ptr, fold_idx, logp_out, nullptr, nullptr, resid_out, cov_out)
+                           : cv_run<float>(gp, 1, nullptr, nullptr, n_folds, fold_ptr, fold_idx, logp_out, nullptr, nullptr, resid_out, cov_out);
+}
+
+int gpmi_cvfold_grad(gpmi_gp* gp, const gpmi_kernel* k, const double* log_noise, int64_t n_noise, int64_t n_folds, const int64_t* fold_ptr,
+                     const int64_t* fold_idx, double* logp_out, double* dkern_out, int32_t n_kern, double* dnoise_out) {
+    if (!gp || !k) return earg((gp ? gp->ctx : nullptr), "gpmi_cvfold_grad: bad argument");
+    if (int rc = cv_check(gp, "gpmi_cvfold_grad", k, log_noise, n_noise, n_kern, dnoise_out != nullptr, true, n_folds, fold_ptr, fold_idx))
+        return rc;
+    GPMI_HIP(gp->ctx, hipSetDevice(gp->ctx->device));
+    return gp->dtype == 64 ? cv_run<double>(gp, 2, k, log_noise, n_folds, fold_ptr, fold_idx, logp_out, dkern_out, dnoise_out, nullptr, nullptr)
+                           : cv_run<float>(gp, 2, k, log_noise, n_folds, fold_ptr, fold_idx, logp_out, dkern_out, dnoise_out, nullptr, nullptr);
 }
 
 int gpmi_logdet(gpmi_gp* gp, double* out) {

@@ -252,6 +252,10 @@ struct gpmi_gp {
     int64_t xp_cap = 0;
     void* small = nullptr;  // mean / mu / var staging
     int64_t small_cap = 0;
+    void* cv = nullptr;     // cross-validation scratch (cv.hip): O(N + sum of fold sizes squared), grown on demand
+    int64_t cv_cap = 0;
+    void* cvblk = nullptr;  // cross-validation: one padded fold block and its factor / inverse (folds of 65 .. 2048), grown on demand
+    int64_t cvblk_cap = 0;
 };
 
 namespace gpmi {
@@ -428,6 +432,16 @@ int64_t launch_dmll(gpmi_ctx* ctx, const T* x, int64_t n, int d, const T* alpha,
 template <typename T>
 int64_t launch_dmll_rect(gpmi_ctx* ctx, const T* xa, int64_t na, const T* xb, int64_t nb, int d, const T* Wt, int64_t ld,
                          double* partial, int n_hyp);
+// W = (K + noise)^-1 into the lower tiles of gp->g2 from the current factor (the K^-1 block of gpmi_grad, api.hip); gp->g1 is
+// scratch.  Returns true for the chunked product, where the tiles hold -W instead.  Caller: alloc_grad_scratch first.
+template <typename T>
+bool build_kinv(gpmi_gp* gp);
+int alloc_grad_scratch(gpmi_gp* gp, size_t bytes);
+// cross-validation (cv.hip) on a fitted dense handle: mode 0 = LOO logp + gradient, 1 = fold predictions + logp, 2 = fold logp + gradient.
+// Folds are CSR (fold_ptr[n_folds + 1], 0-based fold_idx), validated by the caller.
+template <typename T>
+int cv_run(gpmi_gp* gp, int mode, const gpmi_kernel* k, const double* log_noise, int64_t n_folds, const int64_t* fold_ptr,
+           const int64_t* fold_idx, double* logp_out, double* dkern_out, double* dnoise_out, void* resid_out, void* cov_out);
 // out[s] = sum_b partial[b][s]  (deterministic order)
 void launch_reduce_partials(gpmi_ctx* ctx, const double* partial, int64_t nblocks, int nslots, double* out);
 

@@ -15,6 +15,8 @@ from .priors import Normal, Uniform, get_priors, prior_gradlogpdf, prior_logpdf,
 from . import priors  # noqa: F401
 from .means import Mean, MeanConst, MeanLin, MeanPeriodic, MeanPoly, MeanZero, ProdMean, SumMean  # noqa: F401
 from .sparse import FullyIndepPDMat, FullyIndepStrat  # noqa: F401
+from .crossvalidation import (dlogpdtheta_CVfold, dlogpdtheta_LOO, dlogpdθ_CVfold, dlogpdθ_LOO, logp_CVfold,  # noqa: F401
+                              predict_CVfold)
 
 
 def cov(kernel, X1, X2=None, dtype="float64", ctx=None):

@@ -27,7 +27,7 @@ SYMBOLS = [
     "gpmi_solve", "gpmi_whiten", "gpmi_logdet", "gpmi_factor_to_host", "gpmi_factor_diag",
     "gpmi_profile_enable", "gpmi_profile_get", "gpmi_profile_get_bytes", "gpmi_mfma_peak", "gpmi_bench_gemm",
     "gpmi_comm_create_callbacks", "gpmi_comm_unique_id", "gpmi_comm_create_rccl", "gpmi_comm_destroy", "gpmi_comm_selftest", "gpmi_gp_create_blocked",
-    "gpmi_gp_blocked_info", "gpmi_update_alpha",
+    "gpmi_gp_blocked_info", "gpmi_update_alpha", "gpmi_loo_grad", "gpmi_cvfold_predict", "gpmi_cvfold_grad",
 ]
 
 
@@ -123,6 +123,10 @@ def load():
     lib.gpmi_whiten.argtypes = [vp, i64, vp]
     lib.gpmi_logdet.argtypes = [vp, C.POINTER(dbl)]
     lib.gpmi_inv_diag.argtypes = [vp, vp]
+    lib.gpmi_loo_grad.argtypes = [vp, C.POINTER(GpmiKernel), C.POINTER(dbl), i64, C.POINTER(dbl), C.POINTER(dbl), C.c_int32, C.POINTER(dbl)]
+    lib.gpmi_cvfold_predict.argtypes = [vp, i64, vp, vp, vp, vp, C.POINTER(dbl)]
+    lib.gpmi_cvfold_grad.argtypes = [vp, C.POINTER(GpmiKernel), C.POINTER(dbl), i64, i64, vp, vp, C.POINTER(dbl), C.POINTER(dbl), C.c_int32,
+                                     C.POINTER(dbl)]
     lib.gpmi_factor_to_host.argtypes = [vp, vp]
     lib.gpmi_factor_diag.argtypes = [vp, vp]
     lib.gpmi_profile_enable.argtypes = [vp, C.c_int]

@@ -279,6 +279,26 @@ class GPE:
         mu, s2 = self.predict_LOO()
         return float(np.sum(-0.5 * np.log(2.0 * np.pi * s2) - 0.5 * (self.y - mu) ** 2 / s2))
 
+    # -- the rest of src/crossvalidation.jl (gpmi355x.crossvalidation) ---------------------
+    def dlogpdθ_LOO(self, *, noise, domean, kern):
+        from .crossvalidation import dlogpdθ_LOO
+        return dlogpdθ_LOO(self, noise=noise, domean=domean, kern=kern)
+
+    def predict_CVfold(self, folds):
+        from .crossvalidation import predict_CVfold
+        return predict_CVfold(self, folds)
+
+    def logp_CVfold(self, folds):
+        from .crossvalidation import logp_CVfold
+        return logp_CVfold(self, folds)
+
+    def dlogpdθ_CVfold(self, folds, *, noise, domean, kern):
+        from .crossvalidation import dlogpdθ_CVfold
+        return dlogpdθ_CVfold(self, folds, noise=noise, domean=domean, kern=kern)
+
+    dlogpdtheta_LOO = dlogpdθ_LOO
+    dlogpdtheta_CVfold = dlogpdθ_CVfold
+
     # -- rand(gp, x, n) : src/GP.jl:120-146 (posterior branch) ------------------------
     def rand(self, x, n=1, nugget=1e-10, rng=None):
         """Posterior draws at the columns of x: μ + unwhiten(Σ + nugget·I, randn) with (μ, Σ) = predict_f(full_cov=true).

@@ -19,7 +19,8 @@ using GaussianProcesses: GPE, GPBase, Kernel, Mean, EmptyData, CovarianceStrateg
     SEIso, SEArd, Mat12Iso, Mat12Ard, Mat32Iso, Mat32Ard, Mat52Iso, Mat52Ard, RQIso, RQArd,
     Noise, Const, SumKernel, ProdKernel, Masked, FixedKernel, get_value, AbstractGradientPrecompute, SparseStrategy, SparsePDMat
 import GaussianProcesses: alloc_cK, update_cK!, update_mll!, num_params, get_alpha_u, predictMVN, predict_f, mat, cholfactors,
-    init_precompute, precompute!, dmll_kern!, dmll_noise, predict_LOO, KernelData
+    init_precompute, precompute!, dmll_kern!, dmll_noise, predict_LOO, KernelData,
+    dlogpdθ_LOO, predict_CVfold, logp_CVfold, dlogpdθ_CVfold
 using Statistics: mean                 # GaussianProcesses extends Statistics.mean for mean(m::Mean, X)  (src/GaussianProcesses.jl:8)
 using PDMats
 import PDMats: dim, whiten!, whiten, unwhiten!
@@ -301,6 +302,62 @@ function predict_LOO(a::HIPPDMat, alpha::AbstractVector{<:Real}, y::AbstractVect
     return -alpha .* σi2 .+ y, σi2
 end
 Base.Matrix(a::HIPPDMat) = (U = UpperTriangular(cholfactors(a)); Matrix(U' * U))
+# The rest of src/crossvalidation.jl on the device (gpmi_loo_grad / gpmi_cvfold_predict / gpmi_cvfold_grad; DESIGN.md §7b): methods
+# more specific than the reference's, selected by the HIPPDMat covariance as predict_LOO above.  Folds are 1-based here, as there;
+# they go to the C ABI as 0-based CSR.  Mean-parameter gradients throw, as the reference does.
+function cv_folds(folds)
+    ptr = Int64[0]; idx = Int64[]
+    for V in folds
+        append!(idx, Int64.(V) .- 1); push!(ptr, length(idx))
+    end
+    ptr, idx
+end
+function cv_grad(gp::GPE, folds; noise::Bool, domean::Bool, kern::Bool)
+    (domean && num_params(gp.mean) > 0) && throw("I don't know how to do means yet")
+    nfull = full_nparams(gp.kernel)
+    lnv = get_value(gp.logNoise)
+    ln = lnv isa Real ? Float64[lnv] : Vector{Float64}(lnv)
+    (noise && length(ln) != 1) && throw(ArgumentError("the noise gradient needs a scalar logNoise"))
+    dk = Vector{Float64}(undef, max(nfull, 1)); dn = Ref{Float64}(NaN); lp = Ref{Float64}(NaN)
+    dnp = noise ? dn : Ptr{Float64}(C_NULL)
+    rc = withkernel(descriptor(gp.kernel)) do ck
+        if folds === nothing
+            ccall((:gpmi_loo_grad, libgpmi), Cint, (Ptr{Cvoid}, Ref{CKernel}, Ptr{Float64}, Int64, Ref{Float64}, Ptr{Float64}, Int32, Ptr{Float64}),
+                  gp.cK.handle, ck, ln, length(ln), lp, dk, nfull, dnp)
+        else
+            ptr, idx = cv_folds(folds)
+            ccall((:gpmi_cvfold_grad, libgpmi), Cint, (Ptr{Cvoid}, Ref{CKernel}, Ptr{Float64}, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ref{Float64},
+                  Ptr{Float64}, Int32, Ptr{Float64}), gp.cK.handle, ck, ln, length(ln), length(ptr) - 1, ptr, idx, lp, dk, nfull, dnp)
+        end
+    end
+    check(context(), rc)
+    out = Float64[]
+    noise && push!(out, dn[])
+    kern && append!(out, dk[full_slots(gp.kernel)])
+    out
+end
+dlogpdθ_LOO(gp::GPE{X,Y,M,K,HIPCovariance}; noise::Bool, domean::Bool, kern::Bool) where {X,Y,M,K} =
+    cv_grad(gp, nothing; noise=noise, domean=domean, kern=kern)
+dlogpdθ_CVfold(gp::GPE{X,Y,M,K,HIPCovariance}, folds::AbstractVector{<:AbstractVector{Int}}; noise::Bool, domean::Bool, kern::Bool) where {X,Y,M,K} =
+    cv_grad(gp, folds; noise=noise, domean=domean, kern=kern)
+function cv_predict(gp::GPE, folds, want_cov::Bool)
+    ptr, idx = cv_folds(folds)
+    s = diff(ptr)
+    resid = Vector{Float64}(undef, ptr[end]); cov = Vector{Float64}(undef, want_cov ? sum(s .^ 2) : 0); lp = Ref{Float64}(NaN)
+    check(context(), ccall((:gpmi_cvfold_predict, libgpmi), Cint, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ref{Float64}),
+                           gp.cK.handle, length(s), ptr, idx, resid, want_cov ? cov : Ptr{Float64}(C_NULL), lp))
+    resid, cov, s, lp[]
+end
+function predict_CVfold(gp::GPE{X,Y,M,K,HIPCovariance}, folds::AbstractVector{<:AbstractVector{Int}}) where {X,Y,M,K}
+    resid, cov, s, _ = cv_predict(gp, folds, true)
+    μ = Vector{Float64}[]; Σ = Matrix{Float64}[]; o = 0; q = 0
+    for (V, sv) in zip(folds, s)
+        push!(μ, gp.y[V] .- resid[o+1:o+sv]); push!(Σ, reshape(cov[q+1:q+sv*sv], sv, sv))
+        o += sv; q += sv * sv
+    end
+    μ, Σ
+end
+logp_CVfold(gp::GPE{X,Y,M,K,HIPCovariance}, folds::AbstractVector{<:AbstractVector{Int}}) where {X,Y,M,K} = cv_predict(gp, folds, false)[4]
 # unwhiten!(a, x) = L x with a = L Lᵀ (PDMats; the reference's only call is rand!, src/GP.jl:136, on the P x P predictive
 # covariance — a plain PDMat — so this method is for completeness of the AbstractPDMat surface: host product with the
 # fetched factor).  tr(a) as SubsetOfRegsPDMat defines it (subsetofregressors.jl:61-72): trace of the covariance itself,

@@ -5,7 +5,8 @@
  *   predict_f        (cross-cov -> whiten -> mean / variance)
  * and, as the "next" rows of SURVEY.md 8(f) built on the same kernels:
  *   update_dmll!     (gpmi_grad), FITC update_mll! / predict_f (gpmi_fitc_*),
- *   predict_LOO      (gpmi_inv_diag).
+ *   predict_LOO      (gpmi_inv_diag),
+ *   dlogpdθ_LOO, predict_CVfold, logp_CVfold, dlogpdθ_CVfold (gpmi_loo_grad, gpmi_cvfold_predict, gpmi_cvfold_grad).
  * The reference has no FFI; its seam is Julia dispatch on CovarianceStrategy /
  * AbstractPDMat (src/GP.jl:10-20).  Each entry point below names the reference
  * code it replaces (paths relative to the reference repository root); the
@@ -236,6 +237,25 @@ GPMI_API int gpmi_whiten(gpmi_gp*, int64_t nrhs, void* b_inout); /* L^-1 b,  L =
  * (SURVEY 8f rank 4).  n^3/3 flops on the device instead of the reference's dense inverse. */
 GPMI_API int gpmi_inv_diag(gpmi_gp*, void* out);
 GPMI_API int gpmi_logdet(gpmi_gp*, double* out);                 /* 2 sum log U_ii       */
+
+/* ---- cross-validation on a fitted dense handle (src/crossvalidation.jl) ----------------------------------------
+ * Conventions of gpmi_grad: the fit's kernel and log_noise, n_kern = the kernel's parameter count, NULL outputs skipped, the noise
+ * gradient only for scalar logNoise.  Folds are CSR: fold_ptr[n_folds + 1] (fold_ptr[0] = 0), fold_idx 0-based; folds are non-empty,
+ * disjoint, at most GPMI_CV_MAX_FOLD indices each; indices in no fold are training data of every fold.  Dense exact handles only
+ * (blocked / sharded handles: GPMI_EARG).  A fold whose block of (K + noise)^-1 fails to factor: GPMI_ENOTPD.
+ * Device memory: gpmi_grad's two n x n buffers plus O(n + sum of fold sizes squared); factor and alpha are left as they were. */
+#define GPMI_CV_MAX_FOLD 2048
+/* logp_LOO + dlogpdθ_LOO (crossvalidation.jl:50-58, 67-175): dkern_out[p] = d logp_LOO / d theta_p, dnoise_out = d / d logNoise */
+GPMI_API int gpmi_loo_grad(gpmi_gp*, const gpmi_kernel*, const double* log_noise, int64_t n_noise, double* logp_out, double* dkern_out,
+                           int32_t n_kern, double* dnoise_out);
+/* predict_CVfold + logp_CVfold (:180-248): per fold, in fold order, resid_out = W_VV^-1 alpha_V (sum s entries; mu_V = y_V - resid),
+ * cov_out = W_VV^-1 column-major s x s blocks back to back (sum s^2 entries; NULL = skip), W = (K + noise)^-1; dtype of the handle */
+GPMI_API int gpmi_cvfold_predict(gpmi_gp*, int64_t n_folds, const int64_t* fold_ptr, const int64_t* fold_idx, void* resid_out,
+                                 void* cov_out, double* logp_out);
+/* logp_CVfold + dlogpdθ_CVfold (:226-341) */
+GPMI_API int gpmi_cvfold_grad(gpmi_gp*, const gpmi_kernel*, const double* log_noise, int64_t n_noise, int64_t n_folds,
+                              const int64_t* fold_ptr, const int64_t* fold_idx, double* logp_out, double* dkern_out, int32_t n_kern,
+                              double* dnoise_out);
 /* U_out: n x n col-major with the upper factor in its upper triangle and zeros
  * below (== Cholesky(factors,'U',0), src/GPE.jl:60).                        */
 GPMI_API int gpmi_factor_to_host(gpmi_gp*, void* U_out);
